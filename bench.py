@@ -12,10 +12,19 @@ process per GPU: an external torchrun, or bench.py starts the N ranks itself
 when launched without one), every rank merges its own independent document
 (seed + rank): documents shard by id with no data-path collective, so the
 scaling is weak; the only collectives are the timing barrier and max. With
-N > 1 the config-5 line (RCCL all-gather of op logs + sharded merge) rides
-along under "exchange".
+N > 1 and `--full` the config-5 line (RCCL all-gather of op logs + sharded
+merge) rides along under "exchange".
 
     python bench.py --gpus N --steps K --warmup W [--workload flat10m|deep10m|deep10m_il|cfg2|trees|incr|incr_cfg2]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, the merge path taken). `--dump-outputs DIR`
+also writes what the last timed step computed as DIR/<name>.npy. Everything
+else the benchmark measures (per-kernel device times and the roofline, live
+PMC traffic, the stream-copy ceiling, guard G, the CPU baselines, the
+incremental workloads' comparison with a fresh merge, config 5 beside a
+multi-GPU run and its second exchange mode) runs only with `--full`.
 """
 import argparse
 import ctypes as C
@@ -88,6 +97,50 @@ def stream_copy_gbs(dev, nbytes=1 << 30, reps=5):
     gbs = 2 * nbytes * reps / (e0.elapsed_time(e1) / 1e3) / 1e9
     del a, b
     return gbs
+
+
+DUMP_CAP = 4_000_000  # elements per dumped array (float64: 32 MB); a larger output is sampled
+
+
+def dump_array(args, rank, world, name, a):
+    """--dump-outputs: one output array as DIR/<name>.npy (float64; with N
+    ranks every rank writes <name>_rank<r>.npy). An array above DUMP_CAP
+    elements is cut to a fixed, seeded sample of its elements, in order."""
+    a = np.asarray(a)
+    if a.size > DUMP_CAP:
+        a = a.reshape(-1)[np.sort(np.random.default_rng(0xD0C5).choice(a.size, DUMP_CAP, replace=False))]
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if world > 1 else "") + ".npy"),
+            a.astype(np.float64))
+
+
+def dump_tree(args, rank, world, L, tree, res):
+    """--dump-outputs of a single-document step: what its caller holds after
+    the last crdtm_apply. `result`: the crdtm_result (code, path_taken,
+    err_index, n_applied, n_already, timestamp, n_slots, guard, flags);
+    `replicas`: the replicas Dict as (id, timestamp) rows; `document`: the
+    visible nodes' value handles in document order; `canonical`: word count
+    and FNV-1a hash (high and low 32 bits) of the structure dump and of the
+    visible-document dump (crdtm_tree_canonical which = 0, 1)."""
+    from crdtm import _native as N
+    dump_array(args, rank, world, "result", [res.code, res.path_taken, res.err_index, res.n_applied, res.n_already,
+                                             res.timestamp, res.n_slots, res.guard, res.flags])
+    n = C.c_uint64()
+    N.check(L.crdtm_tree_replicas(tree, None, None, 0, C.byref(n)), "replicas")
+    ids, tss = np.zeros(max(n.value, 1), np.int64), np.zeros(max(n.value, 1), np.int64)
+    N.check(L.crdtm_tree_replicas(tree, ids.ctypes.data_as(C.c_void_p), tss.ctypes.data_as(C.c_void_p), n.value,
+                                  C.byref(n)), "replicas")
+    dump_array(args, rank, world, "replicas", np.stack([ids[:n.value], tss[:n.value]], axis=1))
+    N.check(L.crdtm_tree_document(tree, None, 0, C.byref(n)), "document")
+    doc = np.zeros(max(n.value, 1), np.uint32)
+    N.check(L.crdtm_tree_document(tree, doc.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "document")
+    dump_array(args, rank, world, "document", doc[:n.value])
+    canon = []
+    for which in (0, 1):
+        nw, hh = C.c_uint64(), C.c_uint64()
+        N.check(L.crdtm_tree_canonical(tree, which, None, 0, C.byref(nw), C.byref(hh)), "canonical")
+        canon.append([nw.value, hh.value >> 32, hh.value & 0xFFFFFFFF])
+    dump_array(args, rank, world, "canonical", canon)
 
 
 def head(s, m):
@@ -339,7 +392,7 @@ def launch_ranks(n):
 
 
 def want_pmc(args, world):
-    return args.pmc == "on" or (args.pmc == "auto" and world == 1 and not args.pmc_child)
+    return args.full and (args.pmc == "on" or (args.pmc == "auto" and world == 1 and not args.pmc_child))
 
 
 def dry_run(args, rank, world):
@@ -409,12 +462,20 @@ def main():
     ap.add_argument("--workload", default="flat10m", choices=sorted(WORKLOADS) + ["trees", "incr", "incr_cfg2"])
     ap.add_argument("--docs-per-gpu", type=int, default=0, help="trees workload: override documents per GPU")
     ap.add_argument("--n-ops", type=int, default=0, help="override the batch size (parity/debug only)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="oracle sample ops (0 = skip)")
-    ap.add_argument("--profile-steps", type=int, default=3)
-    ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline figure: per-kernel "
+                         "times and the roofline, live PMC traffic, the stream-copy ceiling, guard G, the CPU "
+                         "baselines, the incremental workloads' check against a fresh merge, config 5 beside a "
+                         "multi-GPU run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; large arrays as a "
+                         "fixed, seeded sample)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="with --full: oracle sample ops (0 = skip)")
+    ap.add_argument("--profile-steps", type=int, default=3, help="with --full: untimed per-kernel timing steps")
+    ap.add_argument("--verbose", action="store_true", help="with --full: per-kernel times on stderr")
     ap.add_argument("--exchange", choices=("auto", "on", "off"), default="auto",
                     help="also run config 5 (op-log all-gather + sharded merge) after a single-document "
-                         "workload and attach its line as 'exchange' (auto: when N > 1)")
+                         "workload and attach its line as 'exchange' (auto: when N > 1, with --full)")
     ap.add_argument("--exchange-mode", choices=("both", "all_to_all", "all_gather"), default="both",
                     help="config 5's op-log exchange at N > 1: all_to_all by document owner, north_star's "
                          "all_gather of every log, or both (the step timed with each; all_to_all is `value`)")
@@ -422,7 +483,8 @@ def main():
                     help="every merge takes the one-lane sequential replay (env CRDTM_FORCE_REPLAY=1): "
                          "measures the fallback cliff on the same batch")
     ap.add_argument("--pmc", choices=("auto", "on", "off"), default="auto",
-                    help="measure HBM traffic per step live with rocprofv3 --pmc child passes (auto: 1 GPU)")
+                    help="with --full: measure HBM traffic per step live with rocprofv3 --pmc child passes "
+                         "(auto: 1 GPU)")
     ap.add_argument("--pmc-child", choices=("step", "base"), default=None, help=argparse.SUPPRESS)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher plumbing only, no GPU: ranks (gloo), timing barrier, max over ranks and the "
@@ -470,9 +532,8 @@ def main():
     spec["seed"] = spec["seed"] + rank  # an independent document per rank
     s = N.synth(**spec)
     n = len(s["kind"])
-    B_alg = alg_bytes(s)
 
-    dev = torch.device("cuda", local_rank)
+    dev =torch.device("cuda", local_rank)
     tens = {k: torch.from_numpy(s[k]).to(dev) for k in ("kind", "ts", "path_off", "path", "val")}
     ops = N.Ops(n, int(s["path_off"][n]), tens["kind"].data_ptr(), tens["ts"].data_ptr(),
                 tens["path_off"].data_ptr(), tens["path"].data_ptr(), tens["val"].data_ptr(), None)
@@ -518,6 +579,56 @@ def main():
     guard = res.guard
     serial = {"ops": int(res.serial_ops), "dicts": int(res.serial_dicts), "largest": int(res.serial_max)}
 
+    if args.dump_outputs:  # the state the last timed step left
+        dump_tree(args, rank, world, L, tree, res)
+
+    ms_step = elapsed / args.steps * 1e3
+    value = world * n * args.steps / elapsed
+    serial["fraction_of_ops"] = serial["ops"] / n
+    line = {
+        "metric": "merged ops/sec (whole node) on 10M-op batch",
+        "value": value,
+        "unit": "ops/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic (deterministic generator, SURVEY.md §8d)",
+        "config": {"workload": f"{args.workload}: {n} ops per GPU, one document per GPU",
+                   "replicas": spec.get("replicas"), "window": spec.get("window", 0),
+                   "path": {1: "closed-form", 2: "replay", 3: "per-dict replay"}.get(path_taken, "?"),
+                   "guard": guard, "serial_replay": serial,
+                   "parallelism": f"documents sharded by id over {world} GPU(s)"},
+    }
+    if args.full:
+        full_single(args, rank, world, dev, L, ctx, step, s, n, path_taken, ms_step, line)
+    L.crdtm_tree_destroy(tree)
+    L.crdtm_ctx_destroy(ctx)
+    del tens
+    # The single-document workloads exchange nothing between ranks; config 5 is
+    # the path with the RCCL all-gather, so a multi-GPU run measures it too and
+    # carries its line (same clocks, same contract) under "exchange".
+    if args.exchange == "on" or (args.exchange == "auto" and world > 1 and args.full):
+        ex = run_trees(args, rank, world, local_rank, cpu=False, dump=False)
+        line["exchange"] = {k: ex[k] for k in ("metric", "value", "unit", "ms_per_step", "config")}
+        if args.full:
+            line["exchange"]["roofline_frac"] = ex["roofline"]["frac"]
+            line["exchange"]["all_gather_ms"] = ex["all_gather_ms"]  # (the exchange alone: all_to_all or all_gather)
+            line["exchange"]["modes"] = ex["exchange_modes"]  # (each mode's whole step and exchange alone)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_single(args, rank, world, dev, L, ctx, step, s, n, path_taken, ms_step, line):
+    """--full after a single-document workload's timed steps: per-kernel device
+    times, guard G, the roofline (live PMC traffic, stream-copy ceiling) and
+    the CPU baselines, added to `line`."""
     # Per-kernel device time (HIP events recorded on the launch stream) over a
     # few extra, untimed steps.
     L.crdtm_ctx_profile(ctx, 1)
@@ -550,40 +661,18 @@ def main():
                        "note": "an Add fails guard G when its findInsertion walk meets a Tombstone above its "
                                "timestamp; a dict's ops before its first failing Add are what a closed-form "
                                "prefix could serve (the rest needs the in-order replay)"}
+    line["config"]["guard_g"] = guard_g
     # a kernel launched several times per step is summed within the step
     ps = max(1, args.profile_steps)
     per_step = {nm: sum(v) / ps for nm, v in acc.items()}
     launches = {nm: len(v) for nm, v in acc.items()}
-
-    ms_step = elapsed / args.steps * 1e3
-    value = world * n * args.steps / elapsed
     # SURVEY.md 8d (config 2): how much of the merge ran as in-order replay, and its device-time share
     serial_ms = sum(v for nm, v in per_step.items() if nm.startswith(("k_pdr_small", "k_pdr_big", "k_pdr_huge",
                                                                         "k_pdr_blk", "k_replay")))
     serial_ms -= per_step.get("k_replay_index", 0.0)
-    serial["time_share"] = serial_ms / max(1e-9, sum(per_step.values()))
-    serial["fraction_of_ops"] = serial["ops"] / n
-    line = {
-        "metric": "merged ops/sec (whole node) on 10M-op batch",
-        "value": value,
-        "unit": "ops/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int64",
-        "data": "synthetic (deterministic generator, SURVEY.md §8d)",
-        "config": {"workload": f"{args.workload}: {n} ops per GPU, one document per GPU",
-                   "replicas": spec.get("replicas"), "window": spec.get("window", 0),
-                   "path": {1: "closed-form", 2: "replay", 3: "per-dict replay"}.get(path_taken, "?"),
-                   "guard": guard, "serial_replay": serial, "guard_g": guard_g,
-                   "parallelism": f"documents sharded by id over {world} GPU(s)"},
-        "roofline": roofline(args.workload, per_step, launches, B_alg, ms_step, ps,
-                             live=pmc_live(args) if (rank == 0 and want_pmc(args, world)) else None),
-    }
+    line["config"]["serial_replay"]["time_share"] = serial_ms / max(1e-9, sum(per_step.values()))
+    line["roofline"] = roofline(args.workload, per_step, launches, alg_bytes(s), ms_step, ps,
+                                live=pmc_live(args) if (rank == 0 and want_pmc(args, world)) else None)
     if rank == 0:
         sc = stream_copy_gbs(dev)
         line["roofline"]["stream_copy_gbs"] = sc
@@ -600,22 +689,6 @@ def main():
                                             f"first {m} ops of the same batch (cost grows with the batch)")
             if args.workload == "flat10m":
                 line["cpu_baseline"]["cpp_flat_full_batch"] = cpu_flat_full(s, n)
-    L.crdtm_tree_destroy(tree)
-    L.crdtm_ctx_destroy(ctx)
-    del tens
-    # The single-document workloads exchange nothing between ranks; config 5 is
-    # the path with the RCCL all-gather, so a multi-GPU run measures it too and
-    # carries its line (same clocks, same contract) under "exchange".
-    if args.exchange == "on" or (args.exchange == "auto" and world > 1):
-        ex = run_trees(args, rank, world, local_rank, cpu=False)
-        line["exchange"] = {k: ex[k] for k in ("metric", "value", "unit", "ms_per_step", "config")}
-        line["exchange"]["roofline_frac"] = ex["roofline"]["frac"]
-        line["exchange"]["all_gather_ms"] = ex["all_gather_ms"]  # (the exchange alone: all_to_all or all_gather)
-        line["exchange"]["modes"] = ex["exchange_modes"]  # (each mode's whole step and exchange alone)
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 def run_incr(args, rank, world, local_rank):
@@ -689,7 +762,7 @@ def run_incr(args, rank, world, local_rank):
         return out
 
     want = None
-    if not args.pmc_child:  # the expected state: one fresh merge of base ++ batches
+    if args.full and not args.pmc_child:  # the expected state: one fresh merge of base ++ batches
         fresh = C.c_void_p()
         N.check(L.crdtm_tree_create(ctx, 0, C.byref(fresh)), "tree")
         N.check(L.crdtm_apply(fresh, C.byref(ops_at(0, n)), 1, 1, None, C.byref(res)), "apply")
@@ -724,34 +797,9 @@ def run_incr(args, rank, world, local_rank):
         elapsed += time.perf_counter() - t0
         if check_each:
             print("step state", canon(tree) == want, canon(tree), want, file=sys.stderr, flush=True)
-    # per-kernel device time of one incremental batch (the last one of a step)
-    rebuild()
-    for o in batches[:-1]:
-        apply(o)
-    L.crdtm_ctx_profile(ctx, 1)
-    apply(batches[-1])
-    names = C.create_string_buffer(1 << 16)
-    ms = (C.c_double * 512)()
-    k = L.crdtm_ctx_phase_times(ctx, names, len(names), ms, 512)
-    labels = names.raw.split(b"\0")
-    L.crdtm_ctx_profile(ctx, 0)
-    per_k, launches = {}, {}
-    for j in range(min(k, 512)):
-        nm = labels[j].decode()
-        per_k[nm] = per_k.get(nm, 0.0) + ms[j]
-        launches[nm] = launches.get(nm, 0) + 1
-    # the state the batches built, against one fresh merge of base ++ batches
-    # (the re-merge path): structure and visible document, hash and size
-    verified = canon(tree) == want
-    if not verified:
-        raise RuntimeError(f"incremental state differs from the fresh merge of the same ops: {canon(tree)} {want}")
+    if args.dump_outputs:  # the state the last timed step's batches built
+        dump_tree(args, rank, world, L, tree, res)
     ms_step = elapsed / args.steps * 1e3
-    # SURVEY.md 8d algorithmic bytes of the step's nb batches (Add 49 + 8L, Delete 9 + 8L)
-    a0 = base
-    B_alg = alg_bytes({"kind": s["kind"][a0:], "path_off": s["path_off"][a0:]})
-    # the kernels of the profiled batch (the step's last), times the batches of a step
-    per_k = {k: v * nb for k, v in per_k.items()}
-    launches = {k: v * nb for k, v in launches.items()}
     line = {
         "metric": "merged ops/sec (whole node) on 10M-op batch",
         "value": world * bsz * nb * args.steps / elapsed, "unit": "ops/s", "n_gpus": world, "steps": args.steps,
@@ -768,25 +816,53 @@ def run_incr(args, rank, world, local_rank):
                    "paths": {({1: "closed-form", 2: "replay", 3: "per-dict replay"}).get(p_, "?"): c_
                              for p_, c_ in acct["paths"].items()},
                    "ms_per_batch": ms_step / nb,
-                   "verified": "final state == fresh merge of base ++ batches (structure + document hashes)",
                    "parallelism": f"one document per GPU ({world} GPU(s)), replicas only"},
-        "roofline": roofline(args.workload, per_k, launches, B_alg, ms_step, 1,
-                             live=pmc_live(args) if (rank == 0 and want_pmc(args, world)) else None),
     }
-    line["roofline"]["note"] = ("per step (all its batches): achieved = the batches' algorithmic bytes / step "
-                                "time; kernel times are the profiled last batch x batches per step")
-    if rank == 0 and world == 1:
-        m = args.cpu_sample if args.cpu_sample >= 0 else CPU_SAMPLE["cfg2" if nested else "flat10m"]
-        if m > 0:
-            line["cpu_baseline"] = cpu_line(cpu_baseline(s, min(m, n)),
-                                            f"first {min(m, n)} ops of the same stream, one op at a time (a CPU "
-                                            f"replica merges incrementally at this per-op cost or worse)")
+    if args.full:
+        # per-kernel device time of one incremental batch (the last one of a step)
+        rebuild()
+        for o in batches[:-1]:
+            apply(o)
+        L.crdtm_ctx_profile(ctx, 1)
+        apply(batches[-1])
+        names = C.create_string_buffer(1 << 16)
+        ms = (C.c_double * 512)()
+        k = L.crdtm_ctx_phase_times(ctx, names, len(names), ms, 512)
+        labels = names.raw.split(b"\0")
+        L.crdtm_ctx_profile(ctx, 0)
+        per_k, launches = {}, {}
+        for j in range(min(k, 512)):
+            nm = labels[j].decode()
+            per_k[nm] = per_k.get(nm, 0.0) + ms[j]
+            launches[nm] = launches.get(nm, 0) + 1
+        # the state the batches built, against one fresh merge of base ++ batches
+        # (the re-merge path): structure and visible document, hash and size
+        verified = canon(tree) == want
+        if not verified:
+            raise RuntimeError(f"incremental state differs from the fresh merge of the same ops: {canon(tree)} {want}")
+        line["config"]["verified"] = "final state == fresh merge of base ++ batches (structure + document hashes)"
+        # SURVEY.md 8d algorithmic bytes of the step's nb batches (Add 49 + 8L, Delete 9 + 8L)
+        a0 = base
+        B_alg = alg_bytes({"kind": s["kind"][a0:], "path_off": s["path_off"][a0:]})
+        # the kernels of the profiled batch (the step's last), times the batches of a step
+        per_k = {k: v * nb for k, v in per_k.items()}
+        launches = {k: v * nb for k, v in launches.items()}
+        line["roofline"] = roofline(args.workload, per_k, launches, B_alg, ms_step, 1,
+                                    live=pmc_live(args) if (rank == 0 and want_pmc(args, world)) else None)
+        line["roofline"]["note"] = ("per step (all its batches): achieved = the batches' algorithmic bytes / step "
+                                    "time; kernel times are the profiled last batch x batches per step")
+        if rank == 0 and world == 1:
+            m = args.cpu_sample if args.cpu_sample >= 0 else CPU_SAMPLE["cfg2" if nested else "flat10m"]
+            if m > 0:
+                line["cpu_baseline"] = cpu_line(cpu_baseline(s, min(m, n)),
+                                                f"first {min(m, n)} ops of the same stream, one op at a time (a CPU "
+                                                f"replica merges incrementally at this per-op cost or worse)")
     L.crdtm_tree_destroy(tree)
     L.crdtm_ctx_destroy(ctx)
     return line
 
 
-def run_trees(args, rank, world, local_rank, cpu=True):
+def run_trees(args, rank, world, local_rank, cpu=True, dump=True):
     """Config 5: the simulated replicas' op logs exchanged by document owner
     (RCCL all_to_all_single; document t -> rank t mod world), then every rank
     merges the documents it owns."""
@@ -863,6 +939,25 @@ def run_trees(args, rank, world, local_rank, cpu=True):
     ok_docs = int(np.sum(code == 0))
     if ok_docs != n_mine:  # every generated document merges; anything else is a regression
         raise RuntimeError(f"forest merge: {n_mine - ok_docs} of {n_mine} documents returned an error")
+    if args.dump_outputs and dump:  # what the last timed crdtm_forest_apply returned, per document
+        dump_array(args, rank, world, "doc_code", code)
+        dump_array(args, rank, world, "doc_applied", applied)
+    ms_step = elapsed / args.steps * 1e3
+    line = {
+        "metric": "merged ops/sec (whole node) on 10M-op batch",
+        "value": world * n * args.steps / elapsed, "unit": "ops/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "int64", "data": "synthetic (deterministic generator, SURVEY.md §8d)",
+        "config": {"workload": f"trees: {n_mine} documents x {per} ops per GPU ({n} ops), {n_docs} documents total",
+                   "replicas": TREES["replicas"], "documents_ok": ok_docs,
+                   "parallelism": f"documents sharded by id over {world} GPU(s); op logs exchanged by owner "
+                                  f"({ex.mode}, RCCL)",
+                   "exchange_mode": ex.mode, "recv_bytes_per_rank": ex.recv_bytes,
+                   "used_bytes_per_rank": int(n * shard.REC_W * 8)},
+    }
+    if not args.full:
+        L.crdtm_ctx_destroy(ctx)
+        return line
     # dominant kernel time (HIP events on the launch stream)
     L.crdtm_ctx_profile(ctx, 1)
     step()
@@ -917,23 +1012,10 @@ def run_trees(args, rank, world, local_rank, cpu=True):
     ot = state["ops_t"]
     kinds = ot["kind"][:n].cpu().numpy()
     B_alg = int(np.sum(np.where(kinds == 0, 57, 17)))  # flat documents: L = 1
-    ms_step = elapsed / args.steps * 1e3
-    line = {
-        "metric": "merged ops/sec (whole node) on 10M-op batch",
-        "value": world * n * args.steps / elapsed, "unit": "ops/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "int64", "data": "synthetic (deterministic generator, SURVEY.md §8d)",
-        "config": {"workload": f"trees: {n_mine} documents x {per} ops per GPU ({n} ops), {n_docs} documents total",
-                   "replicas": TREES["replicas"], "documents_ok": ok_docs,
-                   "parallelism": f"documents sharded by id over {world} GPU(s); op logs exchanged by owner "
-                                  f"({ex.mode}, RCCL)",
-                   "exchange_mode": ex.mode, "recv_bytes_per_rank": ex.recv_bytes,
-                   "used_bytes_per_rank": int(n * shard.REC_W * 8)},
-        "roofline": roofline("trees", per_k, launches, B_alg, ms_step, 1,
-                             live=pmc_live(args) if (cpu and rank == 0 and want_pmc(args, world)) else None),
-        "all_gather_ms": ag_ms,
-        "exchange_modes": modes,
-    }
+    line["roofline"] = roofline("trees", per_k, launches, B_alg, ms_step, 1,
+                                live=pmc_live(args) if (cpu and rank == 0 and want_pmc(args, world)) else None)
+    line["all_gather_ms"] = ag_ms
+    line["exchange_modes"] = modes
     if args.verbose and rank == 0:
         for nm, v in sorted(per_k.items(), key=lambda kv: -kv[1])[:12]:
             print(f"  {nm:28s} {v:9.3f} ms", file=sys.stderr)

@@ -17,7 +17,7 @@ for rep in $(seq 1 ${REPS:-2}); do
     elif [[ $v == ab:* ]]; then envs="CRDTM_AB=${v#ab:}"; name=ab_${v#ab:};
     elif [[ $v == env:* ]]; then envs="${v#env:}"; name=$(echo ${v#env:} | tr '=/ ' '___'); fi
     f=gpurun_out/${T}_${W}_${name}_$rep.log
-    env $envs timeout -k 10 300 python -u bench.py --workload $W --steps ${STEPS:-10} --cpu-sample 0 --pmc off --verbose > $f 2>&1 || { echo FAIL $v; tail -5 $f; exit 1; }
+    env $envs timeout -k 10 300 python -u bench.py --workload $W --steps ${STEPS:-10} --full --cpu-sample 0 --pmc off --verbose > $f 2>&1 || { echo FAIL $v; tail -5 $f; exit 1; }
     echo "$name $rep $(grep -o '"ms_per_step": [0-9.]*' $f | head -1)"
   done
 done

@@ -12,7 +12,7 @@ R=$1; shift
 O=gpurun_out
 mkdir -p $O
 for w in "$@"; do
-  timeout -k 10 400 python3 -u bench.py --workload $w > $O/${R}_${w}_bench.log 2>&1 || { echo "FAIL bench $w"; tail -5 $O/${R}_${w}_bench.log; exit 1; }
+  timeout -k 10 400 python3 -u bench.py --workload $w --full > $O/${R}_${w}_bench.log 2>&1 || { echo "FAIL bench $w"; tail -5 $O/${R}_${w}_bench.log; exit 1; }
   echo "$w $(grep -o '"ms_per_step": [0-9.]*' $O/${R}_${w}_bench.log | head -1)"
   bash tools/profile_workload.sh $R $w || { echo "FAIL profile $w"; exit 1; }
   # (a step of the single-document workloads starts at the tree reset, whose
