@@ -23,6 +23,7 @@ FLAG_INCR_WINDOWS = 4  # ... and blocks of its gapped order were spread over reb
 FLAG_INCR_DENSE = 8  # ... and no window could take it: merged densely, the blocks rebuilt
 FLAG_INCR_TOUR = 32  # ... and some gap was ordered as its tree's DFS (keys growing along its anchors)
 FLAG_DICT_INCR = 16  # non-fresh tree: replayed per children dict on the state itself, level by level (ilr.hip)
+FLAG_RANGES_SAMPLED = 64  # fresh flat batch: replica ranges from a sample of its ends, verified by the merge
 REF_NONE = 2 ** 64 - 1
 REF_ROOT = 2 ** 64 - 2
 REL_PARENT, REL_NEXT, REL_PREV, REL_HEAD = 0, 1, 2, 3

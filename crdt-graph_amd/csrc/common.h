@@ -101,7 +101,9 @@ struct DevResult {
   // of the own replica, +3 ops that need per-op statuses (empty path, ts 0)
   uint32_t fl_part[16 * 32];
   uint32_t spec_fail;       // flat speculation: some op is not an Add with a one-element path (k_fl_claim<VERIFY>)
-  uint32_t pre_done;        // k_pre_ts: workgroups finished (the last lays the ranges out)
+  uint32_t pre_done;        // k_pre_sample: workgroups finished (the last lays the ranges out)
+  uint32_t pre_done_full;   // k_pre_ts (the full pass behind a sample that did not suffice): the same
+  uint32_t pre_sampled;     // the sampled ranges sum to n: k_pre_ts returned at once, the claim's counters decide
   uint32_t fl_nw;           // flat order: words of 64 slots, (range_total + 63) / 64
   uint32_t run_count;       // flat order: ep-runs (scan total)
   uint32_t run_fail;        // flat order: the run tree is deeper than RUN_MAXD (generic list ranking instead)

@@ -246,29 +246,39 @@ __global__ void __launch_bounds__(BLOCK) k_path_range(OpsDev o, DevResult* dres)
 // The flat speculation's pre-pass (launched when every op may be an Add with
 // a one-element path, n_path == n): the per-replica counter ranges of the
 // timestamps (16-byte loads, ids below REP_SPEC in an LDS table), |ts| < 2^53,
-// negative timestamps and the largest replica id, and the check that every
-// op is an Add whose path is path[i] alone (kind, path_off[i] == i; else
-// DevResult::spec_fail). The workgroup that finishes last lays the ranges end
-// to end (base[], range_total, the slot words fl_nw), so the claim follows on
-// the device without a host round trip.
+// negative timestamps and the largest replica id. The workgroup that finishes
+// last lays the ranges end to end (base[], range_total, the slot words fl_nw),
+// so the claim follows on the device without a host round trip. The kinds and
+// path offsets are the claim's to check (k_fl_claim<VERIFY>).
+//
+// Two launches share this body. The sample pass (k_pre_sample) folds the
+// timestamp pairs [0, pa) and [pb, n / 2) only — the first and last S ops of
+// the batch — and, when its laid-out total equals n with no negative or
+// out-of-range timestamp and every replica id below REP_SPEC, sets
+// DevResult::pre_sampled. Ranges folded from a subset of the ops are
+// sub-ranges of the exact ones, and a batch the speculation keeps is dense
+// and duplicate-free (its exact range sizes sum to n), so sampled ranges
+// that sum to n are the exact ones of every batch that is kept; the claim's
+// counters (every op in its replica's range, as many slots as ops) decide
+// whether it is. The full pass (k_pre_ts, launched behind the sample when
+// the sample is not the whole batch) returns at once when pre_sampled is set;
+// otherwise it folds every timestamp on top of what the sample left (min/max
+// atomics: idempotent) and lays out the exact ranges.
 constexpr uint32_t REP_SPEC = 256;
-// BLIND: every op's min/max goes to the LDS table as a no-return atomic
-// (nothing to wait for) instead of a read first and an atomic only when the
-// read does not cover it (a typing replica's counters rise through the
-// batch, so its maximum moves on nearly every op anyway)
-template <uint32_t PB, bool BLIND>
-__global__ void __launch_bounds__(PB) k_pre_ts(const long long* __restrict__ ts, const uint8_t* __restrict__ kind,
-                                               const uint32_t* __restrict__ off, uint32_t n, uint2* rng,
-                                               uint32_t* base, DevResult* dres) {
+constexpr uint32_t PRE_SAMPLE = 32768;  // ops per end of the batch (8k / 32k / 128k timed)
+template <uint32_t PB, bool SAMPLE>
+__device__ __forceinline__ void pre_ts_body(const long long* __restrict__ ts, uint32_t n, uint32_t pa, uint32_t pb,
+                                            uint32_t mark, uint2* rng, uint32_t* base, DevResult* dres) {
   __shared__ uint32_t rlo[REP_SPEC], rhi[REP_SPEC];
   __shared__ uint32_t s_last;
   __shared__ unsigned long long sw[PB / 64];
+  if (!SAMPLE && __hip_atomic_load(&dres->pre_sampled, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
   for (uint32_t j = threadIdx.x; j < REP_SPEC; j += PB) {
     rlo[j] = NONE;
     rhi[j] = 0;
   }
   __syncthreads();
-  uint32_t bad = 0, neg = 0, maxr = 0, vfail = 0;
+  uint32_t bad = 0, neg = 0, maxr = 0;
   auto fold = [&](long long t) {
     if (t >= TWO53 || t <= -TWO53) {
       bad = 1;
@@ -278,50 +288,33 @@ __global__ void __launch_bounds__(PB) k_pre_ts(const long long* __restrict__ ts,
       const uint32_t r = static_cast<uint32_t>(static_cast<uint64_t>(t) >> 32), c = static_cast<uint32_t>(t);
       maxr = max(maxr, r);
       if (r < REP_SPEC) {  // (the table only narrows: a covering read makes the atomic unnecessary)
-        if (BLIND || c < rlo[r]) atomicMin(&rlo[r], c);
-        if (BLIND || c > rhi[r]) atomicMax(&rhi[r], c);
+        if (c < rlo[r]) atomicMin(&rlo[r], c);
+        if (c > rhi[r]) atomicMax(&rhi[r], c);
       }
     }
   };
   {
     const longlong2* t2 = reinterpret_cast<const longlong2*>(ts);
-    const uchar2* k2 = reinterpret_cast<const uchar2*>(kind);
-    const uint2* o2 = reinterpret_cast<const uint2*>(off);
-    auto verify = [&](uint32_t p, uchar2 k, uint2 f) {  // ops 2p, 2p + 1
-      vfail |= (k.x | k.y) != CRDTM_ADD || f.x != 2 * p || f.y != 2 * p + 1;
-    };
-    const uint32_t np = n / 2, gs = gridDim.x * PB;
+    // pair j of this launch: [0, pa) as it is, then [pb, n / 2)
+    const uint32_t np = pa + (n / 2 - pb), gs = gridDim.x * PB;
+    auto at = [&](uint32_t j) { return j < pa ? j : pb + (j - pa); };
     uint32_t p = blockIdx.x * PB + threadIdx.x;
     for (; p + 3 * gs < np; p += 4 * gs) {  // four pairs in flight
       longlong2 v[4];
-      uchar2 k[4];
-      uint2 f[4];
 #pragma unroll
-      for (uint32_t u = 0; u < 4; ++u) {
-        v[u] = t2[p + u * gs];
-        k[u] = k2[p + u * gs];
-        f[u] = o2[p + u * gs];
-      }
+      for (uint32_t u = 0; u < 4; ++u) v[u] = t2[at(p + u * gs)];
 #pragma unroll
       for (uint32_t u = 0; u < 4; ++u) {
         fold(v[u].x);
         fold(v[u].y);
-        verify(p + u * gs, k[u], f[u]);
       }
     }
     for (; p < np; p += gs) {
-      const longlong2 v = t2[p];
+      const longlong2 v = t2[at(p)];
       fold(v.x);
       fold(v.y);
-      verify(p, k2[p], o2[p]);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      if (n & 1) {
-        fold(ts[n - 1]);
-        vfail |= kind[n - 1] != CRDTM_ADD || off[n - 1] != n - 1;
-      }
-      vfail |= off[n] != n;
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) fold(ts[n - 1]);
   }
   auto mxf = [](uint32_t a, uint32_t b) { return a > b ? a : b; };
   maxr = block_reduce_t<PB>(maxr, 0u, mxf);  // (synchronises the block)
@@ -332,22 +325,20 @@ __global__ void __launch_bounds__(PB) k_pre_ts(const long long* __restrict__ ts,
     }
   bad = block_reduce_t<PB>(bad, 0u, mxf);
   neg = block_reduce_t<PB>(neg, 0u, mxf);
-  vfail = block_reduce_t<PB>(vfail, 0u, mxf);
   if (threadIdx.x == 0) {
-    if (vfail) atomicOr(&dres->spec_fail, 1u);
     if (bad) atomicOr(&dres->bad_range, 1u);
     if (neg) atomicOr(&dres->has_negative, 1u);
     if (maxr) atomicMax(&dres->max_replica, maxr);
-    // (release: this workgroup's range atomics before its arrival)
-    s_last = __hip_atomic_fetch_add(&dres->pre_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
-             gridDim.x - 1;
+    // (release: this workgroup's range atomics before its arrival; each pass counts its own arrivals)
+    s_last = __hip_atomic_fetch_add(SAMPLE ? &dres->pre_done : &dres->pre_done_full, 1u, __ATOMIC_ACQ_REL,
+                                    __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
   }
   __syncthreads();
   if (!s_last) return;
   // the last workgroup: base[r] = the sizes of the ranges before r (ids above
   // REP_SPEC - 1 make the speculation fail on the host; they are not laid out)
-  const uint32_t nr =
-      min(__hip_atomic_load(&dres->max_replica, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT), REP_SPEC - 1) + 1;
+  const uint32_t mrep = __hip_atomic_load(&dres->max_replica, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+  const uint32_t nr = min(mrep, REP_SPEC - 1) + 1;
   const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x / 64;
   unsigned long long sz = 0;  // (a range spans up to 2^32 counters: sizes and sums in 64 bits)
   if (threadIdx.x < nr) {
@@ -368,7 +359,24 @@ __global__ void __launch_bounds__(PB) k_pre_ts(const long long* __restrict__ ts,
     const uint32_t q = static_cast<uint32_t>(tot < NONE - 64 ? tot : NONE - 64);
     dres->range_total = q;
     dres->fl_nw = (q + 63) / 64;
+    if (SAMPLE && mark) {  // (the sample sufficed, should the batch be one the speculation keeps)
+      const uint32_t b = __hip_atomic_load(&dres->bad_range, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint32_t g = __hip_atomic_load(&dres->has_negative, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      dres->pre_sampled = (tot == n && !b && !g && mrep < REP_SPEC) ? 1u : 0u;
+    }
   }
+}
+// (mark = 0: the sample is the whole batch, pa = pb = n / 2, and the ranges are exact)
+template <uint32_t PB>
+__global__ void __launch_bounds__(PB) k_pre_sample(const long long* __restrict__ ts, uint32_t n, uint32_t pa,
+                                                   uint32_t pb, uint32_t mark, uint2* rng, uint32_t* base,
+                                                   DevResult* dres) {
+  pre_ts_body<PB, true>(ts, n, pa, pb, mark, rng, base, dres);
+}
+template <uint32_t PB>
+__global__ void __launch_bounds__(PB) k_pre_ts(const long long* __restrict__ ts, uint32_t n, uint2* rng,
+                                               uint32_t* base, DevResult* dres) {
+  pre_ts_body<PB, false>(ts, n, n / 2, n / 2, 0u, rng, base, dres);
 }
 
 // Per-op state of the level-synchronous (nested / hash-indexed) path.
@@ -3782,9 +3790,13 @@ static int flat_order_fallback(crdtm_tree* t, uint32_t Q, uint32_t K, FlatBufs& 
 // the result read then checks the batch's shape (SIMPLE, dense, replica ids
 // below REP_SPEC) and returns with *done = false when it is not one this path
 // serves (the caller runs the general path from the top).
+// Sampled ranges (DevResult::pre_sampled, k_pre_sample): kept only when the
+// merge is confirmed as it stands; anything else returns with *done = false
+// and *sampled_miss = true, and the general path serves the batch from exact
+// ranges without a second speculation (no_spec).
 static int apply_flat(crdtm_tree* t, const OpsDev& o, const TsIndex& ix, uint32_t Q, uint32_t maxr, uint8_t* st,
                       uint8_t* st_out, crdtm_result* res, bool simple, RangeReset& rr, bool devq = false,
-                      bool* done = nullptr) {
+                      bool* done = nullptr, bool* sampled_miss = nullptr, bool no_spec = false) {
   if (done) *done = true;
   crdtm_ctx* c = t->ctx;
   hipStream_t s = c->stream;
@@ -3812,7 +3824,7 @@ static int apply_flat(crdtm_tree* t, const OpsDev& o, const TsIndex& ix, uint32_
   };
   // speculation (below): every op applies, so the claim also writes the log
   // (devq: slots up to the bound Q, which the device's range may reach)
-  const bool spec = (devq || Q >= n) && !t->remerge;
+  const bool spec = (devq || Q >= n) && !t->remerge && !no_spec;
   if (spec && (r = grow_for(devq ? Q : n, n))) return r;
   if ((r = flat_rec(c, Q, fb.fr))) return r;
   if (devq) {
@@ -3823,10 +3835,10 @@ static int apply_flat(crdtm_tree* t, const OpsDev& o, const TsIndex& ix, uint32_
   // (16 bytes per replica in the claim's LDS table: up to 3,840 replicas there)
   const uint32_t nrep = maxr + 1 <= HOST_RANGES && maxr + 1 <= 3840 ? maxr + 1 : 0u;
   const uint32_t shm = (4 * nrep + (nrep ? 0 : REP_DIRECT)) * sizeof(uint32_t);
-  // (devq: k_pre_ts has checked the kinds and offsets; k_fl_claim<true, true> checks them itself)
+  // (devq: the claim checks the kinds and path offsets itself, VERIFY)
   static const uint32_t claim_grid = env_grid("CRDTM_CLAIM_GRID", 1024) & ~7u;  // (XCD chunks: a multiple of 8; 1,024 after the LDS staging: 0.610 -> 0.604 ms at flat10m)
   if (simple && spec && devq && nrep)
-    LAUNCH((k_fl_claim<true, false, true>), dim3(std::min(quad_grid(n), std::max(8u, claim_grid))), dim3(BLOCK), shm,
+    LAUNCH((k_fl_claim<true, true, true>), dim3(std::min(quad_grid(n), std::max(8u, claim_grid))), dim3(BLOCK), shm,
            s, o, ix, Q, fb.fr, t->timestamp, c->rtab, dr, 0u, nrep, t->d, 1u);
   else if (simple)
     LAUNCH((k_fl_claim<true, false>), dim3(std::min(quad_grid(n), std::max(8u, claim_grid))), dim3(BLOCK), shm, s, o,
@@ -3876,7 +3888,23 @@ static int apply_flat(crdtm_tree* t, const OpsDev& o, const TsIndex& ix, uint32_
           h.range_total > 4ULL * n + 65536) {
         LAUNCH(k_reset_root, dim3(1), dim3(1), 0, s, t->d.s_next, nullptr);
         *done = false;
+        if (sampled_miss) *sampled_miss = h.pre_sampled != 0;
         return CRDTM_OK;
+      }
+      // sampled ranges are sub-ranges of the exact ones: an op outside them
+      // took no slot (slow), so only a merge confirmed as it stands (every op
+      // in its range, as many slots as ops: the ranges were the exact ones)
+      // is kept; nothing else is decided on them, not even an error code
+      if (h.pre_sampled) {
+        const long long nts = t->timestamp + own - t->own_bias;
+        if (h.bad_range || h.err_index != NONE || slow != 0 || present != keys || keys != n || h.range_total != n ||
+            replica_of(nts) != replica_of(t->timestamp)) {
+          LAUNCH(k_reset_root, dim3(1), dim3(1), 0, s, t->d.s_next, nullptr);
+          *done = false;
+          if (sampled_miss) *sampled_miss = true;
+          return CRDTM_OK;
+        }
+        res->flags |= CRDTM_FLAG_RANGES_SAMPLED;
       }
       // (the shape first: k_pre_ts range-checks every op's ts, a Delete's
       // too, which the reference ignores — a batch with a Delete is not one
@@ -3977,16 +4005,18 @@ static int apply_core(crdtm_tree* t, const OpsDev& o, uint8_t* st_out, crdtm_res
   const bool force_replay = fe && fe[0] == '1';
   // The flat speculation (config 3's shape): a fresh tree and as many path
   // elements as ops, so every op may be an Add whose path is its anchor
-  // alone. The pre-pass reads the timestamps only, the claim checks the
-  // kinds and path offsets, and the whole merge is queued at once with the
-  // slot range read on the device (no host round trip between the pre-pass
-  // and the claim). The result read confirms the shape; a batch of another
-  // shape leaves nothing behind and takes the general path below.
+  // alone. The pre-pass reads timestamps only (a sample of them when that
+  // suffices, k_pre_sample), the claim checks the kinds and path offsets,
+  // and the whole merge is queued at once with the slot range read on the
+  // device (no host round trip between the pre-pass and the claim). The
+  // result read confirms the shape; a batch of another shape leaves nothing
+  // behind and takes the general path below.
   // (env CRDTM_FLAT_SPEC=0: off)
   static const bool spec_on = [] {
     const char* e = getenv("CRDTM_FLAT_SPEC");
     return !(e && e[0] == '0');
   }();
+  bool sampled_miss = false;  // (a speculation on sampled ranges was not confirmed: no second one below)
   if (spec_on && !force_replay && t->n_slots == 1 && t->log_n == 0 && !t->remerge && o.n_path == n) {
     // slot range bound: the radix sort's key width for n (at least 64k
     // slots: small batches with counter gaps), within the dense limit
@@ -3995,17 +4025,29 @@ static int apply_core(crdtm_tree* t, const OpsDev& o, uint8_t* st_out, crdtm_res
     const uint64_t qcap = std::min<uint64_t>(std::max<uint64_t>((1ULL << b) - 2, 65536), 4ULL * n + 65536);
     if (qcap + 2 < (1ULL << FR_ABITS) - 1) {
       if (!dres_ready) LAUNCH(k_dres_init, dim3(1), dim3(64), 0, s, dr);
-      // (env CRDTM_PRE_GRID: workgroups; CRDTM_PRE_BLIND=1: no-return atomics only)
+      // (env CRDTM_PRE_GRID: workgroups of the full pass)
       static const uint32_t pre_grid = env_grid("CRDTM_PRE_GRID", 256);  // (256 x 1024 threads: 55 -> 48 us at flat10m)
-      static const bool pre_blind = [] {
-        const char* e = getenv("CRDTM_PRE_BLIND");
-        return e && e[0] == '1';
-      }();
-      const uint32_t gp = static_cast<uint32_t>(std::min<uint64_t>((n / 2 + PRE_T - 1) / PRE_T + 1, pre_grid));
-      if (pre_blind)
-        LAUNCH((k_pre_ts<PRE_T, true>), dim3(gp), dim3(PRE_T), 0, s, o.ts, o.kind, o.off, n, c->crange, rbase, dr);
-      else
-        LAUNCH((k_pre_ts<PRE_T, false>), dim3(gp), dim3(PRE_T), 0, s, o.ts, o.kind, o.off, n, c->crange, rbase, dr);
+      // The replica ranges come from the first and last S ops (k_pre_sample);
+      // the full pass behind it returns at once on the device when the
+      // sampled ranges sum to n. n <= 2 S: the sample is the whole batch.
+      // (env CRDTM_PRE_SAMPLE=<ops per end>, read on every call; even, the
+      // timestamp loads are 16-byte pairs)
+      uint32_t S = PRE_SAMPLE;
+      if (const char* e = getenv("CRDTM_PRE_SAMPLE")) {
+        const long long v = atoll(e);
+        if (v > 0) S = static_cast<uint32_t>(std::min<long long>(v, 1LL << 30));
+      }
+      S = (S + 1) & ~1u;
+      const bool whole = n <= 2ULL * S;
+      const uint32_t pa = whole ? n / 2 : S / 2, pb = whole ? n / 2 : ((n - S) & ~1u) / 2;
+      const uint32_t gs = static_cast<uint32_t>(
+          std::min<uint64_t>((static_cast<uint64_t>(pa) + (n / 2 - pb) + PRE_T - 1) / PRE_T + 1, pre_grid));
+      LAUNCH(k_pre_sample<PRE_T>, dim3(gs), dim3(PRE_T), 0, s, o.ts, n, pa, pb, whole ? 0u : 1u, c->crange, rbase,
+             dr);
+      if (!whole) {
+        const uint32_t gp = static_cast<uint32_t>(std::min<uint64_t>((n / 2 + PRE_T - 1) / PRE_T + 1, pre_grid));
+        LAUNCH(k_pre_ts<PRE_T>, dim3(gp), dim3(PRE_T), 0, s, o.ts, n, c->crange, rbase, dr);
+      }
       RangeReset spec_clean{c};  // (nr 0: up to the device's max_replica)
       TsIndex ix;
       ix.rng = c->crange;
@@ -4015,7 +4057,7 @@ static int apply_core(crdtm_tree* t, const OpsDev& o, uint8_t* st_out, crdtm_res
       ix.first = nullptr;
       bool done = false;
       int rs = apply_flat(t, o, ix, static_cast<uint32_t>(qcap), REP_SPEC - 1, w.st, st_out, res, true, spec_clean,
-                          true, &done);
+                          true, &done, &sampled_miss);
       if (rs || done) return rs;
     }
   }
@@ -4077,7 +4119,7 @@ static int apply_core(crdtm_tree* t, const OpsDev& o, uint8_t* st_out, crdtm_res
     // (simple: every op an Add whose path is its anchor alone, op i's at path[i])
     if (flat)
       return apply_flat(t, o, ix, static_cast<uint32_t>(range_total), maxr, w.st, st_out, res, o.n_path == n,
-                        keep_clean);
+                        keep_clean, false, nullptr, nullptr, sampled_miss);
     ix.first = ws.alloc<uint32_t>(range_total + 1);
     HIP_CHECK(hipMemsetAsync(ix.first, 0xFF, (range_total + 1) * sizeof(uint32_t), s));
     const uint32_t nrep = maxr + 1 <= HOST_RANGES ? maxr + 1 : 0u;

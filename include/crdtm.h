@@ -96,6 +96,8 @@ typedef struct crdtm_result {
                                      level by level (only the dicts it reaches; ilr.hip) */
 #define CRDTM_FLAG_INCR_TOUR 32   /* with INCREMENTAL: some gap's new nodes were ordered as their tree's DFS
                                      (keys growing along its anchors) instead of replayed one by one */
+#define CRDTM_FLAG_RANGES_SAMPLED 64 /* fresh tree, flat batch: the replica ranges came from a sample of the
+                                        batch's ends (CRDTM_PRE_SAMPLE ops per end), verified by the merge */
 
 typedef struct crdtm_ctx crdtm_ctx;   /* device + stream + workspace */
 typedef struct crdtm_tree crdtm_tree; /* one replica's CRDTree state, resident in HBM */
